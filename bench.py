@@ -158,6 +158,8 @@ def bench_infer(args, P, cfgs, device):
         o = step()
     torch.cuda.synchronize()
     elapsed = time.perf_counter() - t0
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, dict(o=o))        # the waveform of the last timed step: 32 x 1 x 220416 float32, 28 MB
     assert bool(torch.isfinite(o).all())
     P._lib.timer.enabled = True; P._lib.timer.reset()
     for _ in range(2):
@@ -177,6 +179,34 @@ def bench_infer(args, P, cfgs, device):
                 vs_baseline=None, dtype="fp32" if args.fp32 else "bf16", data="synthetic",
                 config=dict(workload=f"C4: infer(), batch {o.size(0)}, T_x = {x.size(1)} tokens, {o.size(-1)} samples per item (durations forced)",
                             parallelism="dp1", execution="eager launches"), roofline=roof)
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+PARAM_SAMPLE = 1 << 22          # elements per network in --dump-outputs (two networks: 32 MB of float32)
+
+
+def param_sample(net, seed):
+    """A fixed, seeded sample (in index order) of every parameter of `net`, flattened in parameters() order, as float32."""
+    import numpy as np
+    flat = torch.cat([p.detach().reshape(-1).float() for p in net.parameters()])
+    if flat.numel() <= PARAM_SAMPLE:
+        return flat
+    idx = np.sort(np.random.default_rng(seed).choice(flat.numel(), PARAM_SAMPLE, replace=False))
+    return flat[torch.from_numpy(idx).to(flat.device)]
+
+
+def dump_outputs(dirname, arrays):
+    """--dump-outputs: DIR/<name>.npy per array (float32, or float64 if computed in float64), at most 64 MB in all."""
+    import numpy as np
+    arrays = {k: v.detach().cpu() for k, v in arrays.items()}
+    arrays = {k: (v.double() if v.dtype == torch.float64 else v.float()).numpy() for k, v in arrays.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_LIMIT_BYTES:
+        raise SystemExit(f"--dump-outputs: {total} bytes exceed the {DUMP_LIMIT_BYTES}-byte limit")
+    os.makedirs(dirname, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(dirname, name + ".npy"), a)
+    print(f"bench: wrote {len(arrays)} arrays ({total} bytes) to {dirname}", file=sys.stderr)
 
 
 def emit(line):
@@ -207,7 +237,11 @@ def main():
     ap.add_argument("--eager", action="store_true", help="launch every kernel from Python instead of replaying the captured hipGraph")
     ap.add_argument("--exchange", action="store_true", help="N = 1 only: run the data-parallel gradient exchange anyway (one-rank RCCL group, "
                     "three graphs with bucket all-reduces between them) to time what that form costs on one GPU")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed as DIR/<name>.npy (seeded inputs: runs compare)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -321,6 +355,10 @@ def main():
             torch.cuda.synchronize(); print(f"step {i} ok", file=sys.stderr, flush=True)
     sync()
     elapsed = time.perf_counter() - t0
+    if args.dump_outputs and rank == 0:
+        # what the last timed step returned (losses, gradient norms) and what it updated (both networks' parameters), before
+        # the untimed legs below step the networks further
+        dump_outputs(args.dump_outputs, dict(out, g_params=param_sample(tuner.net_g, 0), d_params=param_sample(tuner.net_d, 1)))
     # per-kernel roofline leg: the same step, launched eagerly with a HIP event pair around every C-ABI
     # launch of this repo's kernels (events cannot be recorded inside a replayed graph); recorded on the
     # stream the kernels are launched on.  Untimed for the headline, same shapes and data.
@@ -410,7 +448,7 @@ def main():
         if world == 1 and not args.fp32 and not args.no_secondary:
             line["secondary"] = secondary_fp32(tr, hps, device, batch, batch_size)
             # BASELINE.json configs[3] (C4, inference) beside the headline: the same numbers `--workload C4` prints on its own
-            c4 = argparse.Namespace(**{**vars(args), "steps": 5, "warmup": 2})
+            c4 = argparse.Namespace(**{**vars(args), "steps": 5, "warmup": 2, "dump_outputs": None})
             r = bench_infer(c4, P, cfgs, device)
             line["secondary"]["c4_infer"] = {k: r[k] for k in ("metric", "value", "unit", "ms_per_step", "dtype", "config")}
             line["secondary"]["c4_infer"]["roofline_frac"] = r["roofline"]["frac"]

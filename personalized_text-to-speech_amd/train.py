@@ -12,6 +12,7 @@ Differences from the reference, none of which changes a result:
     0-d tensors, discriminator_loss keeps tensors: no host synchronisation inside the step.
 """
 import contextlib
+import os
 
 import torch
 from torch.nn import functional as F
@@ -23,6 +24,15 @@ from .distributed import GradBuckets, broadcast_parameters
 from .losses import discriminator_loss, feature_loss, generator_loss, kl_loss
 from .mel_processing import mel_spectrogram_torch, spec_to_mel_torch
 from .models import MultiPeriodDiscriminator, SynthesizerTrn
+
+
+def graph_branches_supported():
+    """Whether a captured step may keep its side-stream branches as parallel graph branches.  With the HIP runtime's hardware
+    queues capped at two (GPU_MAX_HW_QUEUES, default 4), replaying a step captured with branches crashed the process inside
+    hipGraphLaunch (a host segmentation fault at the first replay, for every captured form of the step), while the same
+    branches run eagerly without fault.  The branches only move launches between streams, so a step recorded on one stream
+    computes the same bits (tests/test_model_gpu.py::test_side_stream_branches_do_not_change_the_step)."""
+    return int(os.environ.get("GPU_MAX_HW_QUEUES", "4")) > 2
 
 
 class FineTuner:
@@ -193,6 +203,7 @@ class FineTuner:
         side-stream branches race, or that depends on memory a replay does not re-initialise, never reaches training."""
         from . import _lib
         assert self.device.type == "cuda" and self._graph is None
+        self._branches_for_capture()
         timer_was, _lib.timer.enabled = _lib.timer.enabled, False
         self._static_batch = batch
         with self.on_capture_stream():
@@ -215,6 +226,7 @@ class FineTuner:
         gradients from the same flat views."""
         from . import _lib
         assert self.device.type == "cuda" and self._graph is None
+        self._branches_for_capture()
         timer_was, _lib.timer.enabled = _lib.timer.enabled, False
         self._static_batch = batch
         with self.on_capture_stream():               # (bench.py at N > 1 warms up itself, the same way: these steps issue collectives)
@@ -239,6 +251,10 @@ class FineTuner:
         if verify:                                   # (collectives inside: every rank captures, so every rank verifies)
             self.verify_replay()
         return self._static_out
+
+    def _branches_for_capture(self):
+        if not graph_branches_supported():
+            self.side_branches = frozenset()
 
     def _state_tensors(self):
         # every parameter and both moments are views of the optimizers' flat buffers
@@ -332,6 +348,7 @@ class FineTuner:
         # Everything — the eager first step of a shape too — runs on ONE non-default stream: autograd keeps the stream of the
         # step that created a parameter's AccumulateGrad node, and a capture that has to synchronise with the legacy default
         # stream is illegal (hipStreamEndCapture crashes on it; FineTuner.capture warms up on a side stream for the same reason).
+        self._branches_for_capture()                              # (before the eager step that warms this shape up)
         cs, cur = self._capture_stream, torch.cuda.current_stream(self.device)
         key = tuple(tuple(t.shape) for t in padded)
         cache = self.__dict__.setdefault("_shape_graphs", {})

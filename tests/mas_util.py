@@ -5,8 +5,8 @@ import numpy as np
 from conftest import ROOT
 
 
-def load_cases():
-    g = np.load(os.path.join(ROOT, "tests", "golden", "mas_cases.npz"))
+def load_cases(fname="mas_cases.npz"):
+    g = np.load(os.path.join(ROOT, "tests", "golden", fname))
     names = sorted({k.split("/")[0] for k in g.files})
     return {n: (g[n + "/neg_cent"], g[n + "/t_ys"], g[n + "/t_xs"], g[n + "/idx"]) for n in names}
 

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Generate tests/golden/mas_cases.npz from the REFERENCE's own Cython DP.
+"""Generate tests/golden/mas_cases.npz and tests/golden/mas_random.npz from the REFERENCE's own Cython DP.
 
 Runs only in the build container (needs oracle/_ref/core*.so, built by `make -C oracle ref`
 from /root/reference/monotonic_align/core.pyx).  Stores, per case, the float32 input
@@ -7,6 +7,7 @@ from /root/reference/monotonic_align/core.pyx).  Stores, per case, the float32 i
 (`idx[b, y]` = the single x with path[b,y,x]==1, -1 for rows y >= t_y).
 
 Cases follow SURVEY.md §8(c): tiny, square, ragged, all-tie, integer-tie, +-1e9 magnitudes.
+mas_random.npz holds 60 seeded random / tie / all-zero items in the same layout (tests/test_mas_oracle.py).
 """
 import os
 import sys
@@ -14,7 +15,9 @@ import sys
 import numpy as np
 
 sys.path.insert(0, os.path.join(os.path.dirname(__file__), ".."))
+sys.path.insert(0, os.path.join(os.path.dirname(__file__), "..", "tests"))
 from oracle import mas as omas  # noqa: E402
+from mas_util import random_case  # noqa: E402
 
 
 def make_cases():
@@ -43,9 +46,18 @@ def make_cases():
     return cases
 
 
-def main():
+def make_random_cases():
+    rng = np.random.default_rng(7)
+    cases = {}
+    for i in range(60):
+        nc, t_ys, t_xs = random_case(rng, 3, int(rng.integers(1, 120)), int(rng.integers(1, 60)), ["normal", "ties", "zeros"][i % 3])
+        cases[f"random{i:02d}"] = (nc, t_ys, np.minimum(t_xs, t_ys))
+    return cases
+
+
+def write(cases, fname):
     out = {}
-    for name, (nc, t_ys, t_xs) in make_cases().items():
+    for name, (nc, t_ys, t_xs) in cases.items():
         path = omas.mas_reference(nc, t_ys, t_xs)
         b, t_t, t_s = nc.shape
         idx = np.full((b, t_t), -1, np.int32)
@@ -57,9 +69,14 @@ def main():
         out[name + "/t_ys"] = t_ys
         out[name + "/t_xs"] = t_xs
         out[name + "/idx"] = idx
-    dst = os.path.join(os.path.dirname(__file__), "..", "tests", "golden", "mas_cases.npz")
+    dst = os.path.join(os.path.dirname(__file__), "..", "tests", "golden", fname)
     np.savez_compressed(dst, **out)
     print("wrote", os.path.abspath(dst), os.path.getsize(dst), "bytes;", len(out) // 4, "cases")
+
+
+def main():
+    write(make_cases(), "mas_cases.npz")
+    write(make_random_cases(), "mas_random.npz")
 
 
 if __name__ == "__main__":
