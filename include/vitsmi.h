@@ -635,6 +635,27 @@ int vits_slice_segments(int elem_bytes, int time_inner, const void* x, const int
                         int t, int seg, int backward, void* stream);
 int vits_generate_path(const float* duration, const float* mask, float* path, int b, int t_y, int t_x, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * vits_expand_prior — the prior expansion of SynthesizerTrn.infer (models.py:507-520: w_ceil, y_lengths, y_mask,
+ *   commons.generate_path, the two one-hot GEMMs and z_p = m + eps * exp(logs) * noise_scale) in one launch (csrc/expand.hip):
+ *     logw      float32 [b][t_x] predicted log-durations, or NULL when `durations` float32 [b][t_x] forces them;
+ *               w_ceil = ceil(exp(logw) * x_mask * length_scale)  |  durations * x_mask, x_mask[x] = x < x_lengths[b];
+ *     x_lengths int64 [b];
+ *     m, logs   the text encoder's statistics, channels-last: row j of item i at m + i*ld_batch + j*ld_row, logs at
+ *               logs_off elements after it (the two halves of one [b][t_x][2c] tensor), s_dtype VITS_DT_F32 | VITS_DT_BF16;
+ *     eps       [b][t_cap][c] standard-normal noise, eps_dtype: VITS_DT_BF16 = the bf16-autocast composition (the GEMMs
+ *               round m and logs to bf16 and the noise is drawn in bf16; exp and the products run in fp32), VITS_DT_F32 = fp32;
+ *     scalars   device float32 [2] = {length_scale, noise_scale} (read by the kernel: one captured graph serves every value);
+ *     z_p       float32 [b][t_cap][c] channels-last, z_p[i][t] = m[tok] + eps * exp(logs[tok]) * noise_scale for
+ *               t < y_len[i] (tok = the token whose frames cover t), 0 beyond — the eager ops' roundings, bit for bit;
+ *     y_mask    float32 [b][t_cap] = t < y_len;  y_lengths int32 [b] = max(sum(w_ceil), 1);  w_ceil int32 [b][t_x].
+ *   t_cap = 0 computes w_ceil and y_lengths only (m, eps, z_p, y_mask may be NULL).  Limits: t_x <= 15360, c % 8 == 0,
+ *   16-byte aligned m / eps / z_p and row pitches.
+ * ------------------------------------------------------------------------------------------ */
+int vits_expand_prior(int s_dtype, int eps_dtype, const float* logw, const float* durations, const int64_t* x_lengths,
+                      const void* m, long ld_row, long ld_batch, int logs_off, const void* eps, const float* scalars, void* z_p,
+                      float* y_mask, int* y_lengths, int* w_ceil, int b, int t_x, int t_cap, int c, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -24,4 +24,5 @@ from . import losses  # noqa: F401
 from . import models  # noqa: F401
 from . import utils  # noqa: F401
 from . import optim  # noqa: F401
+from . import inference  # noqa: F401
 from .models import MultiPeriodDiscriminator, SynthesizerTrn  # noqa: F401

@@ -10,7 +10,7 @@ import subprocess
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "lib", "libvitsmi.so")
-ABI_VERSION = 16
+ABI_VERSION = 17
 
 c_int = ctypes.c_int
 c_void_p = ctypes.c_void_p
@@ -96,6 +96,8 @@ SIGNATURES = {
     "vits_neg_cent": (c_int, [c_int, c_void_p, ctypes.c_long, c_int, c_void_p, c_void_p, ctypes.c_long, c_void_p] + [c_int] * 4 + [c_void_p]),
     "vits_slice_segments": (c_int, [c_int, c_int, c_void_p, c_void_p, ctypes.c_long, c_void_p] + [c_int] * 5 + [c_void_p]),
     "vits_generate_path": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]),
+    "vits_expand_prior": (c_int, [c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, ctypes.c_long, ctypes.c_long, c_int, c_void_p,
+                                  c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p]),
 }
 
 class ConvDesc(ctypes.Structure):

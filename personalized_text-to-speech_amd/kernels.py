@@ -117,6 +117,65 @@ def generate_path(duration, mask):
     return path.view(b, 1, t_y, t_x).to(mask.dtype)
 
 
+def expand_prior(logw, x_lengths, m_p, logs_p, eps, scalars, t_cap, durations=None):
+    """The prior expansion of SynthesizerTrn.infer in one launch (csrc/expand.hip, vits_expand_prior).
+
+    logw [b, 1, t_x] (or durations [b, 1, t_x] forcing the frames per token), x_lengths [b], m_p / logs_p [b, c, t_x] (the text
+    encoder's views of its channels-last [b, t_x, 2c] statistics), eps [b, t_cap, c] (bf16 inside a bf16 autocast region, as
+    infer() draws it there), scalars = device float32 [2] {length_scale, noise_scale}.  Returns z_p [b, t_cap, c] float32
+    channels-last (zero past each item's length), y_mask [b, 1, t_cap] float32, y_lengths [b] int32 and w_ceil [b, t_x] int32.  t_cap = 0: w_ceil and y_lengths only (z_p, y_mask None; m_p, logs_p, eps may be None)."""
+    src = durations if durations is not None else logw
+    _lib.require_cuda(src, x_lengths, scalars)
+    b, t_x = src.size(0), src.size(-1)
+    dev = src.device
+    src = src.detach().reshape(b, t_x).float().contiguous()
+    xl = x_lengths.to(torch.int64).contiguous()
+    assert scalars.dtype == torch.float32 and scalars.numel() == 2 and scalars.is_contiguous()
+    y_lengths = torch.empty(b, dtype=torch.int32, device=dev)
+    w_ceil = torch.empty(b, t_x, dtype=torch.int32, device=dev)
+    z_p = y_mask = None
+    s_dt = o_dt = 0
+    m_ptr = eps_ptr = z_ptr = ym_ptr = None
+    ld_row = ld_batch = logs_off = c = 0
+    if t_cap > 0:
+        _lib.require_cuda(m_p, logs_p, eps)
+        c = m_p.size(1)
+        mc, lc = m_p.detach().transpose(1, 2), logs_p.detach().transpose(1, 2)          # [b, t_x, c] views
+        es = mc.element_size()
+        shared = (mc.dtype == lc.dtype and mc.stride() == lc.stride() and mc.stride(2) == 1
+                  and (lc.data_ptr() - mc.data_ptr()) % es == 0 and (lc.data_ptr() - mc.data_ptr()) // es >= c)
+        if not shared:
+            ml = torch.cat([mc, lc], 2).contiguous()                                          # the [b, t_x, 2c] layout
+            mc, off = ml, c
+        else:
+            off = (lc.data_ptr() - mc.data_ptr()) // es
+        ld_row, ld_batch, logs_off = mc.stride(1), mc.stride(0), off
+        eps_dtype = torch.bfloat16 if torch.is_autocast_enabled() else m_p.dtype          # what the eager GEMMs return
+        if eps_dtype not in (torch.float32, torch.bfloat16) or mc.dtype not in (torch.float32, torch.bfloat16):
+            raise RuntimeError(f"expand_prior: unsupported dtypes {mc.dtype}, {eps_dtype}")
+        e = eps.detach().to(eps_dtype).contiguous()
+        assert tuple(e.shape) == (b, t_cap, c), (tuple(e.shape), (b, t_cap, c))
+        z_p = torch.empty(b, t_cap, c, dtype=torch.float32, device=dev)
+        y_mask = torch.empty(b, 1, t_cap, dtype=torch.float32, device=dev)
+        s_dt, o_dt = _DT[mc.dtype], _DT[eps_dtype]
+        m_ptr, eps_ptr, z_ptr, ym_ptr = mc.data_ptr(), e.data_ptr(), z_p.data_ptr(), y_mask.data_ptr()
+    logw_ptr, dur_ptr = (None, src.data_ptr()) if durations is not None else (src.data_ptr(), None)
+    e0 = _lib.timer.start("vits_expand_prior")
+    rc = _lib.lib().vits_expand_prior(s_dt, o_dt, logw_ptr, dur_ptr, xl.data_ptr(), m_ptr, ld_row, ld_batch, logs_off, eps_ptr,
+                                      scalars.data_ptr(), z_ptr, ym_ptr, y_lengths.data_ptr(), w_ceil.data_ptr(), b, t_x, t_cap, c,
+                                      _lib.stream_ptr())
+    _lib.check(rc, "vits_expand_prior")
+    if z_p is not None:
+        # algorithmic bytes: durations + lengths in, w_ceil + y_lengths out; per frame one gathered m | logs row, eps, z_p and mask
+        # (frames past an item's length read nothing)
+        sb, eb = mc.element_size(), e.element_size()
+        nbytes = b * t_x * 8 + b * 12 + b * t_cap * (c * (2 * sb + eb + 4) + 4)
+    else:
+        nbytes = b * t_x * 8 + b * 12
+    _lib.timer.stop("vits_expand_prior", e0, (0.0, float(nbytes)))
+    return z_p, y_mask, y_lengths, w_ceil
+
+
 def weight_norm(v, g):
     """w = g * v / ||v||_2, norm over every dim but 0 (legacy torch.nn.utils.weight_norm, dim=0;
     reference models.py:254, modules.py:128,135,145,191-206).  For ConvTranspose1d weights
@@ -573,14 +632,29 @@ def lrelu_mask_bwd(dy, y=None, slope=1.0, lengths=None):
 
 
 _workspace = {}
+_retired = []                # superseded workspace buffers a captured graph may still address (kept alive, never reused)
+_graph_captured = False
+
+
+def note_graph_captured():
+    """From now on a captured graph may hold workspace addresses: buffers that workspace() supersedes are retired, not freed."""
+    global _graph_captured
+    _graph_captured = True
 
 
 def workspace(nbytes, device):
     """Grow-only device scratch for the kernels that need one: one buffer per (device, stream), reused in stream order
-    (independent branches of the step run on their own streams and must not share slabs)."""
-    key = (device, torch.cuda.current_stream(device).cuda_stream) if torch.device(device).type == "cuda" else (device, 0)
+    (independent branches of the step run on their own streams and must not share slabs).  Once a graph has been captured
+    (a request during a capture, or note_graph_captured()), a buffer replaced by a larger one goes to `_retired`: the graphs
+    recorded with its address replay into it later."""
+    cuda = torch.device(device).type == "cuda"
+    key = (device, torch.cuda.current_stream(device).cuda_stream) if cuda else (device, 0)
+    if cuda and torch.cuda.is_current_stream_capturing():
+        note_graph_captured()
     buf = _workspace.get(key)
     if buf is None or buf.numel() < nbytes:
+        if buf is not None and _graph_captured:
+            _retired.append(buf)
         buf = torch.empty(max(nbytes, 1 << 20), dtype=torch.uint8, device=device)
         _workspace[key] = buf
     return buf

@@ -655,6 +655,36 @@ class SynthesizerTrn(nn.Module):
         o = self.dec((z * y_mask)[:, :, :max_len], g=g)
         return o, attn, y_mask, (z, z_p, m_p, logs_p)
 
+    # The two stages of a captured inference call (inference.Synthesizer): everything up to the predicted lengths, then — once
+    # the host has read them and chosen a frame capacity — the expansion, the reverse flow and the decoder.  Same arithmetic and
+    # the same noise draws as _infer at equal shapes; the scalars are device tensors so that one captured graph serves every value.
+
+    def _infer_prior(self, x, x_lengths, sid, scalars, durations=None):
+        """Text encoder, speaker embedding, duration predictor (reverse) and the durations.  `scalars` = device float32 [3]
+        {length_scale, noise_scale, noise_scale_w}.  Returns (m_p, logs_p, d, g, y_lengths int32 [b], w_ceil int32 [b, t_x]),
+        d = logw, or the forced durations: what _infer_synth expands."""
+        x, m_p, logs_p, x_mask = self.enc_p(x, x_lengths)
+        g = self._speaker(sid)
+        if self.use_sdp:                        # (also with forced durations: infer() draws this noise either way)
+            logw = self.dp(x, x_mask, g=g, reverse=True, noise_scale=scalars[2])
+        else:
+            logw = self.dp(x, x_mask, g=g)
+        d = durations if durations is not None else logw
+        _, _, y_lengths, w_ceil = K.expand_prior(d, x_lengths, None, None, None, scalars[:2], 0, durations=durations)
+        return m_p, logs_p, d, g, y_lengths, w_ceil
+
+    def _infer_synth(self, m_p, logs_p, d, x_lengths, g, scalars, t_cap, max_len=None, forced=False):
+        """Prior expansion (one kernel: z_p channels-last, zero past each length), reverse flow and decoder at t_cap frames
+        (t_cap >= every predicted length).  The noise is drawn as _infer draws it at t_y = t_cap."""
+        b, c = m_p.size(0), m_p.size(1)
+        dtype = torch.bfloat16 if torch.is_autocast_enabled() else m_p.dtype          # what the eager GEMMs return
+        eps = noise.randn_like(torch.empty(b, t_cap, c, dtype=dtype, device=m_p.device).transpose(1, 2))     # as randn_like(m_p)
+        z_p, y_mask, _, _ = K.expand_prior(None if forced else d, x_lengths, m_p, logs_p, eps.transpose(1, 2), scalars[:2], t_cap,
+                                           durations=d if forced else None)
+        z = self.flow(z_p.transpose(1, 2), y_mask, g=g, reverse=True)
+        o = self.dec((z * y_mask)[:, :, :max_len], g=g)
+        return o, y_mask
+
     def _voice_conversion(self, y, y_lengths, sid_src, sid_tgt):
         assert self.n_speakers > 0, "n_speakers have to be larger than 0."
         g_src = self.emb_g(sid_src).unsqueeze(-1)
